@@ -19,6 +19,13 @@ each round's RCCL collectives itself:
 --parts P (N = 1) runs the same partitioned driver as P parts on ONE GPU, the
 exchanges done by device copies: the single-GPU rehearsal of the N-GPU path.
 
+A plain run sets up, warms up, times --steps steps and prints the result line.
+--full adds, after the clock has stopped, the per-kernel timing pass, the
+per-round profile (`rounds`, `roofline`) and the CPU baseline (`cpu_baseline`).
+--dump-outputs DIR writes what the last timed step computed as .npy files
+(dump_outputs); the inputs are Philox-generated from the arguments, so two
+runs of the same arguments dump the same arrays.
+
 One JSON line on rank 0; see DESIGN.md section 7 for every field.
 """
 from __future__ import annotations
@@ -64,8 +71,8 @@ def parse():
     ap.add_argument("--cpu-sample-n1", type=int, default=0, help="CPU baseline sample size, 1 thread (0: per config)")
     ap.add_argument("--cpu-repeats", type=int, default=5)
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-timing", action="store_true", help="skip per-kernel HIP event timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-timing", action="store_true", help="--full without the per-kernel HIP event timing passes")
     ap.add_argument("--pull-permille", type=int, default=0, help="push/pull switch point (0 = engine default)")
     ap.add_argument("--front-permille", type=int, default=0, help="frontier-bitmap switch point (0 = default)")
     ap.add_argument("--mode", default="auto", choices=["auto", "push", "pull"])
@@ -75,7 +82,15 @@ def parse():
                     help="gossip_set_tuning option for every part (A/B measurements; repeatable)")
     ap.add_argument("--force-partitioned", action="store_true",
                     help="use the library's multi-GPU driver (RCCL collectives) even at WORLD_SIZE 1")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel timing pass, the per-round profile (rounds, "
+                         "roofline) and the CPU baseline; a plain run only times its steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # kernel timer name -> rocprofv3 kernel-name prefix in the PMC summary
@@ -126,6 +141,47 @@ def rounds_to_full(stats: list[dict]) -> int:
         if s["new_receipts"] > 0:
             last = s["round"] + 1
     return last - min(s["round"] for s in stats if s["injected"] > 0) if any(s["injected"] for s in stats) else 0
+
+
+DUMP_SEEN_BYTES = 32 << 20  # seen_sample.npy's size limit (every file of a dump together stays far under 64 MB)
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, stats: list[dict], first_peer: int, seen, coverage, n_msgs: int) -> dict:
+    """--dump-outputs: what a caller of the timed path holds after its last step, as <out_dir>/<name>.npy:
+      round_stats  float64 [rounds, 3 + len(STAT_FIELDS)]: every round's stats record, what gossip_run fills
+                   (round, flags, then _abi.STAT_FIELDS in order; `digest`, a 64-bit hash, as two columns, its
+                   high and its low 32 bits);
+      coverage     float64 [n_msgs]: peers that hold each message, over all the rows read;
+      seen_peers   float64 [k]: the global ids of the sampled peers, ascending;
+      seen_sample  float32 [k, n_msgs]: 1.0 where sampled peer i holds message m (gossip_read_seen's bit m % 64
+                   of word m / 64), else 0.0.
+    The sample is every row when they fit DUMP_SEEN_BYTES, otherwise k rows drawn once, without replacement, by a
+    generator seeded with DUMP_SEED: the same rows in every run of the same arguments.  The counters stay below
+    2^53 in every configuration, so float64 holds them exactly.  Returns {name: shape}."""
+    import numpy as np
+    from gossip_hip._abi import STAT_FIELDS
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rows = seen.shape[0]
+    k = min(rows, max(1, DUMP_SEEN_BYTES // (4 * n_msgs)))
+    if k < rows:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=k, replace=False))
+    else:
+        idx = np.arange(rows)
+    words = np.ascontiguousarray(seen[idx], dtype=np.uint64)
+    bits = (words[:, :, None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)
+    cols = lambda s: [s["round"], s["flags"]] + [  # noqa: E731
+        v for f in STAT_FIELDS for v in ((s[f] >> 32, s[f] & 0xFFFFFFFF) if f == "digest" else (s[f],))]
+    arrays = {
+        "round_stats": np.array([cols(s) for s in stats], dtype=np.float64).reshape(len(stats), 3 + len(STAT_FIELDS)),
+        "coverage": np.asarray(coverage, dtype=np.float64),
+        "seen_peers": (idx + first_peer).astype(np.float64),
+        "seen_sample": bits.reshape(len(idx), -1)[:, :n_msgs].astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def _cpu_model() -> str:
@@ -228,6 +284,9 @@ class Single:
     def last_stats(self):
         return self.eng.last_stats()
 
+    def outputs(self):  # (first global peer of the rows, seen[rows, words], coverage[n_msgs]) after the last step
+        return self.eng.begin, self.eng.read_seen(), self.eng.coverage()
+
     def sync(self):
         import torch
         torch.cuda.synchronize()
@@ -278,6 +337,9 @@ class Grouped(Single):
 
     def last_stats(self):
         return self.g.last_stats()
+
+    def outputs(self):
+        return 0, self.g.read_seen(), self.g.coverage()
 
     def sync(self):
         import torch
@@ -487,11 +549,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    if args.dump_outputs and rank == 0:  # (rank 0's own block under a launcher)
+        dump_outputs(args.dump_outputs, stats, *run.outputs(), w.n_msgs)
+
     deliveries = sum(s["deliveries"] for s in stats)
     value = args.steps * deliveries / dt / 1e9
     roofline = None
     rounds_prof = None
-    if not args.no_timing:
+    if args.full and not args.no_timing:
         from gossip_hip.engine import EXCHANGES, KERNELS
         # per-kernel device times from HIP events on each part's stream, in a separate pass of the same steps
         timed_steps = min(args.steps, 5)
@@ -611,7 +676,7 @@ def main():
                               for r in rounds_prof]
         if roofline:
             line["roofline"] = roofline
-        if run.n_gpus == 1 and run.parts == 1 and dist is None and not args.no_cpu_baseline:
+        if args.full and run.n_gpus == 1 and run.parts == 1 and dist is None and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, args.config)
         print(json.dumps(line), flush=True)
     if isinstance(run, Ranked):

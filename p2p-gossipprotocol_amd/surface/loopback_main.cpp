@@ -40,6 +40,7 @@
 #include <netinet/in.h>
 #include <netinet/tcp.h>
 #include <poll.h>
+#include <sys/resource.h>
 #include <sys/socket.h>
 #include <unistd.h>
 
@@ -221,6 +222,13 @@ int main(int argc, char** argv) {
         if (rp[v] > rp[v + 1] || rp[v + 1] > m) die("bad row_ptr");
     for (uint32_t c : col)
         if (c >= n) die("bad col");
+    // a listener per seed and per peer and two descriptors per edge: a few hundred peers pass the usual soft limit
+    // of 1024 open files, so take what the hard limit allows
+    rlimit nofile{};
+    if (getrlimit(RLIMIT_NOFILE, &nofile) == 0 && nofile.rlim_cur < nofile.rlim_max) {
+        nofile.rlim_cur = nofile.rlim_max;
+        setrlimit(RLIMIT_NOFILE, &nofile);
+    }
 
     // ---- seeds: SeedNode registries behind real listeners ----
     const int q = n_seeds / 2 + 1;  // peer.cpp:64

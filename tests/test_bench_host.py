@@ -131,6 +131,57 @@ def test_link_projection():
     assert b.link_projection(FakeRun(1, 1, []), k_ms[:1], k_b[:1], 2, None) == {}
 
 
+def _stats(rounds):
+    from gossip_hip._abi import STAT_FIELDS
+    return [{"round": r, "flags": r & 1, **{f: 1000 * r + i for i, f in enumerate(STAT_FIELDS)}} for r in range(rounds)]
+
+
+def test_dump_outputs_all_rows(tmp_path):
+    """--dump-outputs with few peers: every row, each message's bit at its own column (80 messages: two words),
+    the stats records in field order with the 64-bit digest as two 32-bit columns."""
+    import numpy as np
+    from gossip_hip._abi import STAT_FIELDS
+    b = _bench()
+    rng = np.random.default_rng(1)
+    held = rng.integers(0, 2, size=(8, 80)).astype(bool)
+    seen = np.zeros((8, 2), dtype=np.uint64)
+    for p, m in zip(*np.nonzero(held)):
+        seen[p, m // 64] |= np.uint64(1) << np.uint64(m % 64)
+    seen[:, 1] |= np.uint64(1) << np.uint64(63)  # a bit past n_msgs: not an output
+    stats = _stats(3)
+    stats[2]["digest"] = 0xFEDCBA9876543210
+    shapes = b.dump_outputs(tmp_path / "out", stats, 0, seen, held.sum(axis=0), 80)
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert set(got) == {"round_stats", "coverage", "seen_peers", "seen_sample"} == set(shapes)
+    assert got["seen_sample"].dtype == np.float32 and np.array_equal(got["seen_sample"], held.astype(np.float32))
+    assert np.array_equal(got["seen_peers"], np.arange(8.0))
+    assert got["coverage"].dtype == np.float64 and np.array_equal(got["coverage"], held.sum(axis=0))
+    rs = got["round_stats"]
+    assert rs.dtype == np.float64 and rs.shape == (3, 3 + len(STAT_FIELDS)) == tuple(shapes["round_stats"])
+    d = 2 + STAT_FIELDS.index("digest")
+    assert list(rs[1, :d]) == [1, 1] + [1000 + i for i in range(d - 2)]
+    assert (int(rs[2, d]), int(rs[2, d + 1])) == (0xFEDCBA98, 0x76543210)
+    assert list(rs[1, d + 2:]) == [1000 + i for i in range(d - 1, len(STAT_FIELDS))]
+
+
+def test_dump_outputs_samples_the_same_rows_within_the_size_limit(tmp_path, monkeypatch):
+    """More rows than fit: a sample of distinct rows, ascending, offset by the block's first peer, the same in every
+    call, each with its own row's bits."""
+    import numpy as np
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_SEEN_BYTES", 4 * 64 * 100)  # room for 100 rows of 64 messages
+    seen = np.arange(5000, dtype=np.uint64).reshape(5000, 1) * np.uint64(0x9E3779B97F4A7C15)
+    for name in ("a", "b"):
+        b.dump_outputs(tmp_path / name, _stats(1), 7000, seen, np.zeros(64), 64)
+    a, c = (np.load(tmp_path / n / "seen_peers.npy") for n in ("a", "b"))
+    assert np.array_equal(a, c) and a.shape == (100,) and np.all(np.diff(a) > 0) and a[0] >= 7000 and a[-1] < 12000
+    bits = np.load(tmp_path / "a" / "seen_sample.npy")
+    assert bits.shape == (100, 64) and bits.nbytes <= 4 * 64 * 100
+    assert np.array_equal(bits, np.load(tmp_path / "b" / "seen_sample.npy"))
+    words = (bits.astype(np.uint64) << np.arange(64, dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
+    assert np.array_equal(words, seen[a.astype(np.int64) - 7000, 0])
+
+
 def test_critical_path_of_side_stream_kernels():
     """A round's critical-path device time: the heavy rows' pull beside a binned round's scatter counts only when
     the round has no heavy_commit (whose timer covers the join)."""

@@ -13,8 +13,8 @@
 #   evidence                 round 6's bounds evidence: the dense-exchange group tests against the checked build
 #                            of round 5's stream kernel (build/checked_unfixed, tools/experiments/
 #                            r06_unmasked_stream_entries.patch); failures are the record, not an error
-#   bench:<config>[:args]    bench.py --config <config> (args: extra bench flags, '+' for spaces)
-#   parts:<P>                bench.py --parts P (config 4 as P vertex blocks on one GPU)
+#   bench:<config>[:args]    bench.py --full --config <config> (args: extra bench flags, '+' for spaces)
+#   parts:<P>                bench.py --full --parts P (config 4 as P vertex blocks on one GPU)
 #   rounds:<config>[:t.k=v]  tools/round_profile.py (per-round kernel times; t.key=value tuning)
 #   prof:<config>            rocprofv3 kernel trace + stats of the bench command, FETCH_SIZE and WRITE_SIZE passes
 #   pmcrounds:<config>[:..]  the same three passes over tools/round_profile.py (tuning args as rounds)
@@ -69,12 +69,12 @@ for step in "$@"; do
       echo "rc=$? (failures expected: GOSSIP_EBOUNDS)"; grep -E "EBOUNDS|index past|passed|failed" $O/evidence.log | cut -c1-300 | head -30 ;;
     bench)
       extra=${a[2]//+/ }
-      timeout -k 10 400 python3 -u bench.py --config ${a[1]} $extra > $O/bench_config${a[1]}.json 2> $O/bench_config${a[1]}.err \
+      timeout -k 10 400 python3 -u bench.py --full --config ${a[1]} $extra > $O/bench_config${a[1]}.json 2> $O/bench_config${a[1]}.err \
         || fail $step $O/bench_config${a[1]}.err
       python3 -c "import json;d=json.loads(open('$O/bench_config${a[1]}.json').read().splitlines()[-1]);r=d['roofline'];print(${a[1]}, d['config']['workload'], d['value'], 'GTEPS', d['ms_per_step'], 'ms', 'frac', r.get('frac'), 'step', r.get('step_frac'), 'cpu', (d.get('cpu_baseline') or {}).get('value'))" ;;
     parts)
       P=${a[1]}
-      timeout -k 10 600 python3 -u bench.py --parts $P --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_parts$P.json 2> $O/bench_parts$P.err \
+      timeout -k 10 600 python3 -u bench.py --full --parts $P --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_parts$P.json 2> $O/bench_parts$P.err \
         || fail $step $O/bench_parts$P.err
       python3 -c "import json; d=json.loads(open('$O/bench_parts$P.json').read().splitlines()[-1]); r=d['roofline']; print($P, d['ms_per_step'], d['value'], r.get('frac'), sum(r.get('kernel_ms_per_step').values()), r.get('exchange_ms_per_step'), r.get('exchange_link_ms_per_step'), r.get('projected_ms_per_step'))" ;;
     rounds)
@@ -83,7 +83,7 @@ for step in "$@"; do
       tail -30 $f | cut -c1-220 ;;
     prof)
       C=${a[1]}; d=$O/prof_c$C; mkdir -p $d
-      timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $d/c${C}_trace -o run -- python3 -u bench.py --config $C --no-cpu-baseline --steps 5 --warmup 1 > $d/bench_trace.json 2> $d/bench_trace.err || fail $step $d/bench_trace.err
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $d/c${C}_trace -o run -- python3 -u bench.py --full --config $C --no-cpu-baseline --steps 5 --warmup 1 > $d/bench_trace.json 2> $d/bench_trace.err || fail $step $d/bench_trace.err
       timeout -s KILL 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $d/c${C}_fetch -o run -- python3 -u bench.py --config $C --no-cpu-baseline --no-timing --steps 3 --warmup 1 > $d/bench_fetch.json 2> $d/bench_fetch.err || fail $step $d/bench_fetch.err
       timeout -s KILL 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $d/c${C}_write -o run -- python3 -u bench.py --config $C --no-cpu-baseline --no-timing --steps 3 --warmup 1 > $d/bench_write.json 2> $d/bench_write.err || fail $step $d/bench_write.err
       pmc_summary $d "bench.py --config $C (gpu.sh $OUT $step)" c$C
