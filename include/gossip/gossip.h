@@ -53,6 +53,13 @@ typedef int gossip_status;
                                            (single partition, one word per peer, slot layout) */
 #define GOSSIP_FLAG_UNIFORM_PARTITION 128u /* gossip_group_create: blocks of ceil(n/parts) peers, rounded up to
                                               whole 64-peer tiles, instead of gossip_partition_edges */
+#define GOSSIP_FLAG_RECEIPT_TRACE 256u /* keep the receipt trace on the device (see "receipt trace" below): 2·M B
+                                          per owned peer for the receipt rounds, 2 B for its death round and 8·W B
+                                          (W padded to 1, 2, 4 or 8) for the shadow of seen the trace kernel compares
+                                          against.  gossip_create: GOSSIP_ENOMEM when that does not fit; GOSSIP_EINVAL
+                                          with rejoin_threshold > 0 (a restart empties a Message-List) or
+                                          max_rounds > 65535 (rounds are kept as u16) */
+#define GOSSIP_NEVER 0xFFFFu           /* receipt / death round of a pair never received / a peer still alive */
 
 /*
  * Replaces: NetworkConfig's parsed values (config.cpp:31-42,93-96) plus the
@@ -303,10 +310,32 @@ gossip_status gossip_read_alive(gossip_ctx* ctx, uint8_t* out);
 /* Seed-registry membership of all n_peers peers (seed.cpp peerList; 1 byte each). */
 gossip_status gossip_read_registered(gossip_ctx* ctx, uint8_t* out);
 
+/* ---- receipt trace (GOSSIP_FLAG_RECEIPT_TRACE) ------------------------------
+ * Replaces the reference's only result, the per-peer log ("Generated message" / "Received new message",
+ * peer.cpp:283,375), at any size.
+ *   receipt[v][m] = the round r in which bit m of v first appears in seen: a receipt in round r's push is
+ *                   recorded as r, a message v generates itself in round r (its origin alive) as r;
+ *                   GOSSIP_NEVER if v never held m.  A peer that dies keeps its entries.
+ *   death[v]      = the round in which v stopped being alive (a peer that failed registration, list_cap:
+ *                   round 0); GOSSIP_NEVER while it lives.
+ * Both are valid between rounds: a read after the step of round r reflects rounds <= r, also when round r
+ * deferred its seen update.  gossip_reset sets every entry back to GOSSIP_NEVER.  Without the flag the
+ * readers return GOSSIP_ESTATE; a range past the owned peers is GOSSIP_EINVAL. */
+/* owned peers [first, first+count) (local indices): out[count * M], row-major, entry m of a row = message m */
+gossip_status gossip_read_receipt_rounds(gossip_ctx* ctx, uint64_t first, uint64_t count, uint16_t* out);
+/* out[count] */
+gossip_status gossip_read_death_rounds(gossip_ctx* ctx, uint64_t first, uint64_t count, uint16_t* out);
+/* hist[rounds][M] over the owned peers: hist[r][m] = owned peers whose entry for m equals r (the per-message
+ * latency distribution, reduced on the device); *rounds = min(rounds run since the reset, max_rounds) */
+gossip_status gossip_read_receipt_histogram(gossip_ctx* ctx, uint64_t* hist, uint32_t max_rounds, uint32_t* rounds);
+/* global peer ids; the range may span blocks */
+gossip_status gossip_group_read_receipt_rounds(gossip_group* g, uint64_t first, uint64_t count, uint16_t* out);
+gossip_status gossip_group_read_death_rounds(gossip_group* g, uint64_t first, uint64_t count, uint16_t* out);
+
 /* ---- measurement ----------------------------------------------------------- */
 /* Per-kernel device time (ms) accumulated since timing was last enabled, by kernel name
  * ("push_light", "push_heavy", "pull_light", "pull_heavy", "frontier_bits", "bin_scatter", "bin_apply",
- * "pb_scatter", "pb_split", "pb_apply", "liveness", "churn", "kills", "inject", "apply_remote"),
+ * "pb_scatter", "pb_split", "pb_apply", "liveness", "churn", "kills", "inject", "apply_remote", "trace", "trace_hist"),
  * measured with HIP events on the ctx stream.  enable != 0 turns timing on. */
 gossip_status gossip_enable_timing(gossip_ctx* ctx, int enable);
 gossip_status gossip_kernel_time(gossip_ctx* ctx, const char* kernel, double* ms, uint64_t* launches);
@@ -321,7 +350,8 @@ gossip_status gossip_kernel_time(gossip_ctx* ctx, const char* kernel, double* ms
  * 16·Wp B per owned peer ("bin_apply"); propagation-blocked rounds: 8 B per owned
  * peer + 24 B per frontier peer + 16 B per traversal ("pb_scatter"), 22 B per
  * traversal ("pb_split"), 10 B per traversal + 24 B per activated peer
- * ("pb_apply"). */
+ * ("pb_apply"); receipt trace: 8·W B per owned peer swept + 2 B per receipt stored
+ * ("trace"), 2·M B per owned peer ("trace_hist"). */
 gossip_status gossip_kernel_bytes(gossip_ctx* ctx, const char* kernel, double* bytes);
 
 /* ---- engineering options ---------------------------------------------------- */
@@ -380,7 +410,8 @@ gossip_status gossip_kernel_bytes(gossip_ctx* ctx, const char* kernel, double* b
  * "heavy_side" (1 default: at P = 1 a binned round's heavy-row pull runs on a
  * second stream beside the scatter and k_heavy_commit applies its finds after
  * the apply; 0: the pull after the apply), "blocked_clear_all" (1 default: wide blocked rounds clear every new word in
- * level 2; 0: level 1 clears the words it consumes).
+ * level 2; 0: level 1 clears the words it consumes), "trace_shape" (the receipt trace's stores: 0 default, one
+ * peer's row per store instruction with lanes as messages; 1: every lane stores into its own peer's row).
  * Layout keys
  * apply at the next gossip_build_graph / gossip_load_csr ("list_cap": at the
  * next chain of needy-list rounds, never inside one).  GOSSIP_EINVAL: unknown key. */

@@ -7,6 +7,10 @@
 // (broadcastMessage/handleClient, peer.cpp:255-318).  For small networks
 // (<= kTraceMax peers) the run is traced so that the reference's per-peer
 // and per-seed log files, message lists and sentTo sets can be reproduced.
+// With SimOptions::device_trace (network.txt: trace=1) the engine keeps the
+// receipt trace on the device (GOSSIP_FLAG_RECEIPT_TRACE): receiptRound() is
+// served from it at any size, and networks of up to 60,000 peers get the
+// reference-format peer logs without a per-round readback.
 #pragma once
 
 #include <atomic>
@@ -41,13 +45,18 @@ struct SimOptions {
     // when fewer GPUs are visible, every part on `device` with device-copy exchange).  Traced
     // networks (<= kTraceMax peers) keep one partition: their per-peer views read the whole overlay.
     uint32_t n_gpus = 1;
-    std::string log_dir;                  // reference-format logs (small networks)
+    std::string log_dir;                  // reference-format logs (small networks; up to 60,000 peers with
+                                          // device_trace)
+    bool device_trace = false;            // network.txt trace=1: the engine keeps per-peer receipt and death rounds
+                                          // on the device (GOSSIP_FLAG_RECEIPT_TRACE); receiptRound() reads them at
+                                          // any size, single partition or group, and captureRound does no per-round
+                                          // seen readback.  Default 0: nothing changes
     std::vector<std::pair<std::string, int>> addresses;  // optional ip:port per peer (default: peer_address())
 
     // Reference keys (ping_interval, message_interval, max_messages,
     // max_missed_pings) plus simulation keys: n_peers, rng_seed, graph,
     // list_len, origins, churn_ppm, max_rounds, min_rounds, kills=p@r,...,
-    // device, n_gpus, log_dir.
+    // device, n_gpus, log_dir, trace.
     static SimOptions fromConfig(const NetworkConfig& cfg);
 };
 
@@ -85,7 +94,8 @@ public:
     bool traced() const { return trace_; }
     std::vector<uint32_t> rowOf(uint64_t id) const;             // out-neighbours (CSR row, bootstrap)
     bool edgeLive(uint64_t id, uint32_t to) const;              // not dropped by liveness
-    long receiptRound(uint64_t id, uint32_t m) const;           // -1: never received / generated
+    // -1: never received / generated.  With device_trace: at any size (from the device trace, between rounds)
+    long receiptRound(uint64_t id, uint32_t m) const;
     std::vector<uint32_t> sentTo(uint64_t id, uint32_t m) const;
 
     void writeLogs(const std::string& dir) const;
@@ -112,6 +122,14 @@ private:
     std::vector<std::vector<uint8_t>> aliveAt_;  // per round (after churn/kills)
     std::vector<int32_t> maskRound_;           // per edge: round masked (-1 live)
     std::vector<int32_t> deathRound_;          // per peer
+
+    // device trace (opt_.device_trace): rows fetched from the engine, cached until the next round
+    mutable std::vector<uint16_t> devRecv_;    // all n * M entries (n <= kDevTraceAll) or one peer's M
+    mutable uint64_t devRecvPeer_ = ~0ull;     // the peer devRecv_ holds (~0: all)
+    mutable size_t devRecvRounds_ = ~(size_t)0;  // rounds_.size() it was read at (~0: nothing cached)
+    static constexpr uint64_t kDevTraceAll = 60000;  // writeLogs' limit: up to here the whole trace is fetched at once
+    bool fetchDeviceTrace(uint64_t id) const;
+    void writeDeviceLogs(const std::string& dir) const;  // n > kTraceMax: logs from the CSR, the reports, the device trace
 
     void captureRound(uint32_t r);
     void seedRemovalsFromReports();  // partitioned runs: each round's removals from the merged reports

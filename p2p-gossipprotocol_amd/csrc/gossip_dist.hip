@@ -1287,6 +1287,32 @@ gossip_status gossip_group_read_seen(gossip_group* g, uint64_t* host_seen) {
     return GOSSIP_OK;
 }
 
+// receipt trace of global peers [first, first + count): every block's share of the window, in block order
+static gossip_status group_read_trace(gossip_group* g, uint64_t first, uint64_t count, uint16_t* out, bool death) {
+    if (!g || (count && !out)) return set_error(GOSSIP_EINVAL, "null argument");
+    if (!(ctx_config(g->d->ranks[0].ctx).flags & GOSSIP_FLAG_RECEIPT_TRACE))
+        return set_error(GOSSIP_ESTATE, "group created without GOSSIP_FLAG_RECEIPT_TRACE");
+    if (first > g->n || count > g->n - first) return set_error(GOSSIP_EINVAL, "range past the peers");
+    const uint64_t per = death ? 1 : ctx_config(g->d->ranks[0].ctx).n_msgs;
+    for (auto& r : g->d->ranks) {
+        const uint64_t lo = std::max(first, r.begin), hi = std::min(first + count, r.begin + r.n_local);
+        if (lo >= hi) continue;
+        uint16_t* dst = out + (lo - first) * per;
+        const gossip_status s = death ? gossip_read_death_rounds(r.ctx, lo - r.begin, hi - lo, dst)
+                                      : gossip_read_receipt_rounds(r.ctx, lo - r.begin, hi - lo, dst);
+        if (s) return s;
+    }
+    return GOSSIP_OK;
+}
+
+gossip_status gossip_group_read_receipt_rounds(gossip_group* g, uint64_t first, uint64_t count, uint16_t* out) {
+    return group_read_trace(g, first, count, out, false);
+}
+
+gossip_status gossip_group_read_death_rounds(gossip_group* g, uint64_t first, uint64_t count, uint16_t* out) {
+    return group_read_trace(g, first, count, out, true);
+}
+
 gossip_status gossip_group_read_reports(gossip_group* g, gossip_dead_report* buf, uint64_t cap, uint64_t* count) {
     if (!g || !count) return set_error(GOSSIP_EINVAL, "null argument");
     std::vector<gossip_dead_report> all;

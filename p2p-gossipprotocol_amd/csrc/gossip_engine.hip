@@ -317,6 +317,12 @@ struct gossip_ctx {
     uint64_t* rep_aux = nullptr;
     uint64_t rep_aux_words = 0, rep_tw = 0, rep_hw = 0;
 
+    // receipt trace (GOSSIP_FLAG_RECEIPT_TRACE, gossip_trace.hip): all null without the flag
+    uint16_t* tr_receipt = nullptr;        // n_local * M receipt rounds (row-major, the ABI's layout)
+    uint16_t* tr_death = nullptr;          // n_local death rounds
+    uint64_t* tr_shadow = nullptr;         // n_local * Wp: the seen bits already recorded
+    uint32_t trace_shape = 0;              // "trace_shape" (A/B)
+
     // library-driven multi-GPU rounds (gossip_dist.hip): the driver that issues
     // this ctx's collectives; owned here for gossip_comm_init, by the group otherwise
     gossip::DistDriver* dist = nullptr;
@@ -529,6 +535,11 @@ void free_state(gossip_ctx* c) {
     hipFree(c->reports);
     hipFree(c->n_reports);
     hipFree(c->inj_live);
+    hipFree(c->tr_receipt);
+    hipFree(c->tr_death);
+    hipFree(c->tr_shadow);
+    c->tr_receipt = c->tr_death = nullptr;
+    c->tr_shadow = nullptr;
     hipFree(c->ex_col);
     hipFree(c->ex_cnt);
     hipFree(c->ex_miss);
@@ -1380,7 +1391,7 @@ gossip_status round_begin(gossip_ctx* c, bool remote, int requested, int* mode) 
 }
 
 // Small overlays run whole in one launch (gossip_tiny.hip) unless they use a feature only the round-by-round
-// engine has (re-bootstrap, join churn, coverage history) or are partitioned.
+// engine has (re-bootstrap, join churn, coverage history, the receipt trace) or are partitioned.
 // (the one-launch run writes every round's stats into one pinned buffer of max_rounds entries: a caller's
 // "no limit" max_rounds runs round by round instead of allocating it)
 constexpr uint32_t kTinyMaxRounds = 1u << 16;
@@ -1388,7 +1399,7 @@ constexpr uint32_t kTinyMaxRounds = 1u << 16;
 bool tiny_ok(const gossip_ctx* c) {
     return !c->tiny_off && c->graph_ready && c->n_local == c->n && c->world <= 1 && !c->dist && !c->gather &&
            c->n <= kTinyPeers && c->n_edges <= kTinyEdges && !c->cfg.extra_cap && !c->cfg.rejoin_threshold &&
-           !c->cov_hist && !c->in_round && c->cfg.max_rounds <= kTinyMaxRounds;
+           !c->cov_hist && !c->tr_receipt && !c->in_round && c->cfg.max_rounds <= kTinyMaxRounds;
 }
 
 TinyArgs tiny_args(gossip_ctx* c) {
@@ -1798,8 +1809,38 @@ gossip_status read_slot(gossip_ctx* c, gossip_round_stats* out, bool cumulative)
     return GOSSIP_OK;
 }
 
+// Receipt trace: the round's receipts and deaths recorded, after everything of the round that can add one
+// (remote applies and the heavy rows' commit included) and before the word buffers rotate.  The kernel takes
+// the fresh bits as (seen | a deferred round's nx) & ~shadow, so it needs no exact buffer and no host read
+// (a replayed round issues it like any other kernel).
+gossip_status trace_round(gossip_ctx* c) {
+    HIPCHK(hipSetDevice(c->device));
+    TraceArgs t{};
+    t.seen = c->seen;
+    t.extra = c->cur_defer ? c->nx : nullptr;
+    t.shadow = c->tr_shadow;
+    t.alive = c->alive;
+    t.receipt = c->tr_receipt;
+    t.death = c->tr_death;
+    t.n_local = c->n_local;
+    t.begin = c->begin;
+    t.M = c->M;
+    t.W = c->W;
+    t.Wp = c->Wp;
+    t.round = c->round;
+    t.shape = c->trace_shape;
+    HIPCHK(timed(c, "trace", [&] { return launch_trace_receipts(t, c->stream); }));
+    if (c->timing) {
+        const double got = c->last_st_round == c->round ? (double)(c->last_st.new_receipts + c->last_st.injected) : 0.0;
+        c->kbytes["trace"] += 8.0 * c->W * (double)c->n_local + 2.0 * got;
+    }
+    return GOSSIP_OK;
+}
+
 gossip_status advance(gossip_ctx* c, uint64_t fresh_global) {
     bool pend = false;
+    if (c->tr_receipt)
+        if (gossip_status ts = trace_round(c)) return ts;
     if (c->cur_defer) {  // every delivery of the round is in nx (remote applies included): fold it into seen
         if (c->world <= 1 && (c->bins_ready || c->pb_ready))
             pend = true;  // after the swap, in nw: the next round folds it (k_bin_apply, k_pb_scatter's or
@@ -1964,6 +2005,12 @@ gossip_status gossip_create(const gossip_config* cfg, gossip_ctx** out) {
         return fail(GOSSIP_EINVAL, "rejoin_threshold needs a single partition");
     if (cfg->graph_model == GOSSIP_GRAPH_REF_BOOTSTRAP && cfg->n_peers > 4096)
         return fail(GOSSIP_EINVAL, "ref_bootstrap supports n_peers <= 4096");
+    if (cfg->flags & GOSSIP_FLAG_RECEIPT_TRACE) {
+        if (cfg->rejoin_threshold)
+            return fail(GOSSIP_EINVAL, "GOSSIP_FLAG_RECEIPT_TRACE cannot be combined with rejoin_threshold > 0");
+        if (cfg->max_rounds > 65535)
+            return fail(GOSSIP_EINVAL, "GOSSIP_FLAG_RECEIPT_TRACE needs max_rounds <= 65535 (rounds are kept as u16)");
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(GOSSIP_ENODEV, "no HIP device visible");
     int dev = cfg->device;
@@ -2042,6 +2089,12 @@ gossip_status gossip_create(const gossip_config* cfg, gossip_ctx** out) {
         if ((err = hipMalloc((void**)&c->cov_hist, (uint64_t)c->cfg.max_rounds * 64 * c->Wp * 8)) != hipSuccess)
             return bail("coverage history", err);
     }
+    if (c->cfg.flags & GOSSIP_FLAG_RECEIPT_TRACE) {
+        if ((err = hipMalloc((void**)&c->tr_receipt, c->n_local * c->M * 2 + 8)) != hipSuccess)
+            return bail("receipt trace", err);
+        if ((err = hipMalloc((void**)&c->tr_death, c->n_local * 2 + 2)) != hipSuccess) return bail("death rounds", err);
+        if ((err = hipMalloc((void**)&c->tr_shadow, words2 * 8)) != hipSuccess) return bail("trace shadow", err);
+    }
     c->n_started = c->n;  // every peer starts until an overlay with a list_cap says otherwise
     if (gossip_status rs = gossip_reset(c)) {
         const std::string m = g_last_error;
@@ -2094,6 +2147,7 @@ gossip_status gossip_set_tuning(gossip_ctx* c, const char* key, int64_t value) {
     else if (k == "apply_wide") c->apply_wide = value != 0;
     else if (k == "scatter_small") c->scatter_small = value != 0;
     else if (k == "blocked_clear_all") c->pb_clear_all = value != 0;
+    else if (k == "trace_shape") c->trace_shape = value == 1 ? 1u : 0u;
     else if (k == "blocked_marks") c->pb_marks = value != 0;
     else if (k == "blocked_pipe") c->pb_pipe = value != 0;
     else if (k == "zero_fill") c->zero_fill = value != 0;
@@ -2431,6 +2485,11 @@ gossip_status gossip_reset(gossip_ctx* c) {
         }
     }
     if (c->cov_hist) HIPCHK(hipMemsetAsync(c->cov_hist, 0, (uint64_t)c->cfg.max_rounds * 64 * c->Wp * 8, s));
+    if (c->tr_receipt) {  // every entry back to GOSSIP_NEVER, nothing recorded
+        HIPCHK(hipMemsetAsync(c->tr_receipt, 0xFF, c->n_local * c->M * 2, s));
+        HIPCHK(hipMemsetAsync(c->tr_death, 0xFF, c->n_local * 2, s));
+        HIPCHK(hipMemsetAsync(c->tr_shadow, 0, words * 8, s));
+    }
     // slots still hold words of the last run: the first binned round of the next rewrites every slot
     c->bins_first = true;
     if (c->cfg.extra_cap) {
@@ -2716,6 +2775,49 @@ gossip_status gossip_read_coverage_history(gossip_ctx* c, uint64_t* buf, uint32_
         }
     if (rounds) *rounds = R;
     return GOSSIP_OK;
+}
+
+// receipt trace readers: a window of owned peers, copied straight from the device rows (the device layout is
+// the ABI's), so one peer's row of a 2^28-peer run is a 2·M-byte copy
+static gossip_status read_trace(gossip_ctx* c, const uint16_t* d, uint64_t per_peer, uint64_t first, uint64_t count,
+                                uint16_t* out) {
+    if (!c || (count && !out)) return fail(GOSSIP_EINVAL, "null argument");
+    if (!c->tr_receipt) return fail(GOSSIP_ESTATE, "ctx created without GOSSIP_FLAG_RECEIPT_TRACE");
+    if (first > c->n_local || count > c->n_local - first) return fail(GOSSIP_EINVAL, "range past the owned peers");
+    if (set_dev(c)) return GOSSIP_EHIP;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (count) HIPCHK(hipMemcpy(out, d + first * per_peer, count * per_peer * 2, hipMemcpyDeviceToHost));
+    return GOSSIP_OK;
+}
+
+gossip_status gossip_read_receipt_rounds(gossip_ctx* c, uint64_t first, uint64_t count, uint16_t* out) {
+    return read_trace(c, c ? c->tr_receipt : nullptr, c ? c->M : 0, first, count, out);
+}
+
+gossip_status gossip_read_death_rounds(gossip_ctx* c, uint64_t first, uint64_t count, uint16_t* out) {
+    return read_trace(c, c ? c->tr_death : nullptr, 1, first, count, out);
+}
+
+gossip_status gossip_read_receipt_histogram(gossip_ctx* c, uint64_t* hist, uint32_t max_rounds, uint32_t* rounds) {
+    if (!c || !hist) return fail(GOSSIP_EINVAL, "null argument");
+    if (!c->tr_receipt) return fail(GOSSIP_ESTATE, "ctx created without GOSSIP_FLAG_RECEIPT_TRACE");
+    if (set_dev(c)) return GOSSIP_EHIP;
+    const uint32_t R = std::min(c->round, max_rounds);
+    if (rounds) *rounds = R;
+    if (!R) return GOSSIP_OK;
+    const uint64_t nb = (uint64_t)R * c->M;
+    unsigned long long* d = nullptr;
+    HIPCHK(hipMalloc((void**)&d, nb * 8));
+    gossip_status st = GOSSIP_OK;
+    hipError_t e = hipMemsetAsync(d, 0, nb * 8, c->stream);
+    if (e == hipSuccess)
+        e = timed(c, "trace_hist", [&] { return launch_trace_hist(c->tr_receipt, c->n_local, c->M, R, d, c->stream); });
+    if (e == hipSuccess) e = hipMemcpyAsync(hist, d, nb * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) st = fail(GOSSIP_EHIP, std::string("receipt histogram: ") + hipGetErrorString(e));
+    hipFree(d);
+    if (!st && c->timing) c->kbytes["trace_hist"] += 2.0 * c->M * (double)c->n_local;
+    return st;
 }
 
 gossip_status gossip_read_reports(gossip_ctx* c, gossip_dead_report* buf, uint64_t cap, uint64_t* count) {

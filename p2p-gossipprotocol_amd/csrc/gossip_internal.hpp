@@ -514,6 +514,24 @@ hipError_t launch_px_pack(const PbArgs& p, uint32_t world, uint32_t own, const u
 hipError_t launch_pb_split(const PbArgs& p, hipStream_t s);
 hipError_t launch_pb_apply(const RoundArgs& a, const PbArgs& p, hipStream_t s);
 
+// ---- receipt trace (gossip_trace.hip; GOSSIP_FLAG_RECEIPT_TRACE) ----
+struct TraceArgs {
+    const uint64_t* seen;     // n_local * Wp
+    const uint64_t* extra;    // a deferred round's receipts (its nx: not in seen yet) or null
+    uint64_t* shadow;         // n_local * Wp: the bits the trace has recorded
+    const uint32_t* alive;    // global bitset
+    uint16_t* receipt;        // n_local * M, row-major (the ABI's layout): receipt round or GOSSIP_NEVER
+    uint16_t* death;          // n_local: death round or GOSSIP_NEVER
+    uint64_t n_local, begin;
+    uint32_t M, W, Wp, round;
+    uint32_t shape;           // "trace_shape": 0 a peer's row per store instruction, 1 a row per lane (A/B)
+};
+constexpr uint64_t kTraceHistLds = 12288;  // k_trace_hist: up to this many (round, message) bins (48 KB) in LDS
+hipError_t launch_trace_receipts(const TraceArgs& t, hipStream_t s);
+// hist[rounds * M] += the owned peers' entries per (round, message)
+hipError_t launch_trace_hist(const uint16_t* receipt, uint64_t n_local, uint32_t M, uint32_t rounds,
+                             unsigned long long* hist, hipStream_t s);
+
 // ---- small overlays (gossip_tiny.hip) ----
 hipError_t launch_tiny_erow(const uint64_t* rp, uint32_t n, uint32_t* erow, hipStream_t s);
 hipError_t launch_tiny_reset(const TinyArgs& t, uint64_t words, uint32_t n_started, bool unmask, uint64_t tact_words,

@@ -35,6 +35,8 @@ FLAG_FORCE_BIN = 16
 FLAG_NO_BLOCKED = 32
 FLAG_FORCE_BLOCKED = 64
 FLAG_UNIFORM_PARTITION = 128
+FLAG_RECEIPT_TRACE = 256
+GOSSIP_NEVER = 0xFFFF
 MODE_AUTO = -1
 MODE_PUSH = 0
 MODE_PULL = 1
@@ -106,6 +108,7 @@ def lib() -> C.CDLL:
     L = C.CDLL(str(LIB_PATH))
     P, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
     pu32, pu64, pu8 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
+    pu16 = C.POINTER(C.c_uint16)
     sigs = {
         "gossip_create": (i32, [C.POINTER(GossipConfig), C.POINTER(P)]),
         "gossip_destroy": (None, [P]),
@@ -138,6 +141,11 @@ def lib() -> C.CDLL:
         "gossip_read_coverage": (i32, [P, pu64]),
         "gossip_read_coverage_history": (i32, [P, pu64, u32, pu32]),
         "gossip_read_reports": (i32, [P, C.POINTER(DeadReport), u64, pu64]),
+        "gossip_read_receipt_rounds": (i32, [P, u64, u64, pu16]),
+        "gossip_read_death_rounds": (i32, [P, u64, u64, pu16]),
+        "gossip_read_receipt_histogram": (i32, [P, pu64, u32, pu32]),
+        "gossip_group_read_receipt_rounds": (i32, [P, u64, u64, pu16]),
+        "gossip_group_read_death_rounds": (i32, [P, u64, u64, pu16]),
         "gossip_read_alive": (i32, [P, pu8]),
         "gossip_read_registered": (i32, [P, pu8]),
         "gossip_enable_timing": (i32, [P, i32]),

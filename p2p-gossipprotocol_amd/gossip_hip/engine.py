@@ -18,7 +18,7 @@ from ._abi import DeadReport, GossipConfig, RoundStats, check
 _GRAPHS = {"powerlaw": _abi.GRAPH_POWERLAW, "ref_bootstrap": _abi.GRAPH_REF_BOOTSTRAP}
 KERNELS = ("push_light", "push_heavy", "push_extra", "src_count", "frontier_bits", "pull_light", "pull_heavy", "pull_list", "list_zero", "bin_scatter",
            "bin_apply", "pb_scatter", "pb_split", "pb_apply", "liveness", "rebootstrap", "rejoin", "churn", "kills",
-           "inject", "apply_remote", "commit", "compact_send", "px_scatter", "tiny", "heavy_commit")
+           "inject", "apply_remote", "commit", "compact_send", "px_scatter", "tiny", "heavy_commit", "trace")
 # kernels that run on a ctx's second stream beside others (binned rounds at P = 1: the heavy rows' pull beside the
 # scatter); a round's critical path counts them only when the round has no join (heavy_commit, whose timer covers
 # the wait for the side stream)
@@ -77,7 +77,8 @@ def make_config(n_peers: int, n_msgs: int, *, rng_seed: int = 0, graph: str = "p
                 part: tuple[int, int] = (0, 0), report_capacity: int = 0, mode: str = "auto",
                 pull_permille: int = 0, front_permille: int = 0, bin_permille: int = 0, bins: bool = True,
                 extra_cap: int = 0, list_cap: int = 0, rejoin_threshold: int = 0, blocked: str = "auto",
-                blocked_permille: int = 0, uniform_partition: bool = False) -> GossipConfig:
+                blocked_permille: int = 0, uniform_partition: bool = False,
+                receipt_trace: bool = False) -> GossipConfig:
     """gossip_config from keyword arguments (the fields of include/gossip/gossip.h)."""
     cfg = GossipConfig()
     cfg.n_peers = n_peers
@@ -96,7 +97,8 @@ def make_config(n_peers: int, n_msgs: int, *, rng_seed: int = 0, graph: str = "p
     cfg.flags = (_abi.FLAG_COVERAGE_HISTORY if coverage_history else 0) | (0 if bins else _abi.FLAG_NO_BIN) | {
         "auto": 0, "push": _abi.FLAG_FORCE_PUSH, "pull": _abi.FLAG_FORCE_PULL, "bin": _abi.FLAG_FORCE_BIN}[mode] | {
         "auto": 0, "off": _abi.FLAG_NO_BLOCKED, "force": _abi.FLAG_FORCE_BLOCKED}[blocked] | (
-        _abi.FLAG_UNIFORM_PARTITION if uniform_partition else 0)
+        _abi.FLAG_UNIFORM_PARTITION if uniform_partition else 0) | (
+        _abi.FLAG_RECEIPT_TRACE if receipt_trace else 0)
     cfg.report_capacity = report_capacity
     cfg.pull_permille = pull_permille
     cfg.front_permille = front_permille
@@ -315,6 +317,33 @@ class Engine:
               "gossip_read_coverage_history")
         return buf[: r.value]
 
+    # receipt trace (receipt_trace=True; GOSSIP_FLAG_RECEIPT_TRACE)
+    def receipt_rounds(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """(count, M) uint16: the round in which owned peer first + i first held message m (GOSSIP_NEVER: never)."""
+        if count is None:
+            count = self.shape()["n_local"] - first
+        out = np.zeros((max(count, 0), self.n_msgs), dtype=np.uint16)
+        check(self._L.gossip_read_receipt_rounds(self._ctx, first, count, _ptr(out, C.c_uint16)),
+              "gossip_read_receipt_rounds")
+        return out
+
+    def death_rounds(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """(count,) uint16: the round in which owned peer first + i died (GOSSIP_NEVER: alive)."""
+        if count is None:
+            count = self.shape()["n_local"] - first
+        out = np.zeros(max(count, 0), dtype=np.uint16)
+        check(self._L.gossip_read_death_rounds(self._ctx, first, count, _ptr(out, C.c_uint16)),
+              "gossip_read_death_rounds")
+        return out
+
+    def receipt_histogram(self, max_rounds: int = 4096) -> np.ndarray:
+        """(rounds, M) uint64: hist[r, m] = owned peers that first held message m in round r (device reduction)."""
+        buf = np.zeros((max_rounds, self.n_msgs), dtype=np.uint64)
+        r = C.c_uint32()
+        check(self._L.gossip_read_receipt_histogram(self._ctx, _ptr(buf, C.c_uint64), max_rounds, C.byref(r)),
+              "gossip_read_receipt_histogram")
+        return buf[: r.value]
+
     def reports(self) -> np.ndarray:
         cnt = C.c_uint64()
         check(self._L.gossip_read_reports(self._ctx, None, 0, C.byref(cnt)), "gossip_read_reports")
@@ -453,6 +482,23 @@ class Group:
         check(self._L.gossip_group_read_reports(self._g, buf.ctypes.data_as(C.POINTER(DeadReport)), cnt.value,
                                                 C.byref(cnt)), "gossip_group_read_reports")
         return buf[: cnt.value]
+
+    # receipt trace over global peer ids (the window may span blocks)
+    def receipt_rounds(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        if count is None:
+            count = self.n_peers - first
+        out = np.zeros((max(count, 0), self.n_msgs), dtype=np.uint16)
+        check(self._L.gossip_group_read_receipt_rounds(self._g, first, count, _ptr(out, C.c_uint16)),
+              "gossip_group_read_receipt_rounds")
+        return out
+
+    def death_rounds(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        if count is None:
+            count = self.n_peers - first
+        out = np.zeros(max(count, 0), dtype=np.uint16)
+        check(self._L.gossip_group_read_death_rounds(self._g, first, count, _ptr(out, C.c_uint16)),
+              "gossip_group_read_death_rounds")
+        return out
 
     def part_ctx(self, p: int) -> C.c_void_p:
         ctx = C.c_void_p()

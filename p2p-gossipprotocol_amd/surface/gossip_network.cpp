@@ -50,6 +50,7 @@ SimOptions SimOptions::fromConfig(const NetworkConfig& c) {
     o.device = (int)c.getInt("device", -1);
     o.n_gpus = (uint32_t)std::max<long long>(1, c.getInt("n_gpus", 1));
     o.log_dir = c.getString("log_dir", "");
+    o.device_trace = c.getInt("trace", 0) != 0;
     return o;
 }
 
@@ -115,6 +116,7 @@ bool GossipNetwork::start() {
     cfg.max_rounds = opt_.max_rounds;
     cfg.min_rounds = opt_.min_rounds;
     cfg.device = opt_.device;
+    if (opt_.device_trace) cfg.flags |= GOSSIP_FLAG_RECEIPT_TRACE;
     trace_ = n <= kTraceMax;
     const uint32_t parts = trace_ ? 1u : std::max<uint32_t>(1, opt_.n_gpus);
     gossip_status st = GOSSIP_OK;
@@ -206,15 +208,17 @@ void GossipNetwork::captureRound(uint32_t r) {
         if (alive_[v] && !alive[v]) deathRound_[v] = (int32_t)r;
     alive_ = alive;
     aliveAt_.push_back(alive);
-    std::vector<uint64_t> seen(n * W_);
-    gossip_read_seen(ctx_, seen.data());
-    for (uint64_t i = 0; i < n * W_; ++i) {
-        for (uint64_t x = seen[i] & ~seen_[i]; x; x &= x - 1) {
-            const uint32_t m = (uint32_t)((i % W_) * 64 + __builtin_ctzll(x));
-            recvRound_[(i / W_) * M_ + m] = (int32_t)r;
+    if (!opt_.device_trace) {  // (with the device trace receiptRound() reads the engine's rows instead)
+        std::vector<uint64_t> seen(n * W_);
+        gossip_read_seen(ctx_, seen.data());
+        for (uint64_t i = 0; i < n * W_; ++i) {
+            for (uint64_t x = seen[i] & ~seen_[i]; x; x &= x - 1) {
+                const uint32_t m = (uint32_t)((i % W_) * 64 + __builtin_ctzll(x));
+                recvRound_[(i / W_) * M_ + m] = (int32_t)r;
+            }
         }
+        seen_.swap(seen);
     }
-    seen_.swap(seen);
     std::vector<uint64_t> rp(n + 1);
     std::vector<uint32_t> col(std::max<size_t>(col_.size(), 1));
     gossip_read_csr(ctx_, rp.data(), col.data());
@@ -263,7 +267,7 @@ bool GossipNetwork::run() {
     while (!finished_ && !stop_) {
         if (step() < 0) return false;
     }
-    if (finished_ && !opt_.log_dir.empty() && trace_) writeLogs(opt_.log_dir);
+    if (finished_ && !opt_.log_dir.empty() && (trace_ || opt_.device_trace)) writeLogs(opt_.log_dir);
     return true;
 }
 
@@ -337,7 +341,30 @@ bool GossipNetwork::edgeLive(uint64_t id, uint32_t to) const {
     return false;
 }
 
+// The device trace's rows for receiptRound(): the whole trace in one read while it is small (up to
+// kDevTraceAll peers), one peer's row otherwise (gossip_read_receipt_rounds takes a range so that a single row
+// of a 2^28-peer run is a 2·M-byte copy); kept until the next round.
+bool GossipNetwork::fetchDeviceTrace(uint64_t id) const {
+    const uint64_t n = opt_.n_peers;
+    const bool all = n <= kDevTraceAll;
+    if (devRecvRounds_ == rounds_.size() && devRecvPeer_ == (all ? ~0ull : id)) return true;
+    devRecvRounds_ = ~(size_t)0;
+    devRecv_.resize((all ? n : 1) * M_);
+    const uint64_t first = all ? 0 : id, count = all ? n : 1;
+    const gossip_status st = group_ ? gossip_group_read_receipt_rounds(group_, first, count, devRecv_.data())
+                                    : gossip_read_receipt_rounds(ctx_, first, count, devRecv_.data());
+    if (st != GOSSIP_OK) return false;
+    devRecvPeer_ = all ? ~0ull : id;
+    devRecvRounds_ = rounds_.size();
+    return true;
+}
+
 long GossipNetwork::receiptRound(uint64_t id, uint32_t m) const {
+    if (opt_.device_trace) {
+        if (!started_ || id >= opt_.n_peers || m >= M_ || !fetchDeviceTrace(id)) return -1;
+        const uint16_t r = devRecv_[(devRecvPeer_ == ~0ull ? id * M_ : 0) + m];
+        return r == GOSSIP_NEVER ? -1 : (long)r;
+    }
     return trace_ ? (long)recvRound_[id * M_ + m] : -1;
 }
 
@@ -357,8 +384,65 @@ std::vector<uint32_t> GossipNetwork::sentTo(uint64_t id, uint32_t m) const {
     return out;
 }
 
+// Networks above kTraceMax with the device trace: the reference-format peer logs written once, at the end of
+// the run, from the CSR (read once), the dead-node reports (a report (round, reporter, dead) is the round the
+// edge reporter -> dead was dropped, peer.cpp:381-397) and the device trace -- the same lines, in the same
+// order, as the per-round host capture produces.
+void GossipNetwork::writeDeviceLogs(const std::string& dir) const {
+    const uint64_t n = opt_.n_peers;
+    std::vector<uint64_t> rp(n + 1, 0);
+    std::vector<uint32_t> col;
+    gossip_ctx* part = ctx_;
+    uint64_t begin = 0;
+    for (uint32_t p = 0; ctx_ ? p < 1 : gossip_group_part(group_, p, &part) == GOSSIP_OK; ++p) {
+        uint32_t words = 0, xw = 0;
+        uint64_t nl = 0, ne = 0;
+        if (gossip_get_shape(part, &words, &xw, &nl, &ne) != GOSSIP_OK || begin + nl > n) return;
+        std::vector<uint64_t> prp(nl + 1);
+        std::vector<uint32_t> pcol(std::max<uint64_t>(ne, 1));
+        if (gossip_read_csr(part, prp.data(), pcol.data()) != GOSSIP_OK) return;
+        const uint64_t base = col.size();
+        for (uint64_t v = 0; v < nl; ++v) rp[begin + v + 1] = base + prp[v + 1];
+        col.insert(col.end(), pcol.begin(), pcol.begin() + ne);
+        begin += nl;
+    }
+    if (begin != n || !fetchDeviceTrace(0)) return;
+    // reports() is sorted by (round, reporter, dead) and rows by neighbour: per reporter, in edge order per round
+    std::map<uint32_t, std::vector<std::pair<uint32_t, uint32_t>>> dropped;  // reporter -> (round, dead)
+    for (const gossip_dead_report& r : reports()) dropped[r.reporter].emplace_back(r.round, r.dead);
+    std::vector<Message> msgs;
+    for (uint32_t m = 0; m < M_; ++m) msgs.push_back(message(m));
+    for (uint64_t v = 0; v < n; ++v) {
+        const PeerInfo me = peerInfo(v);
+        std::ofstream f(dir + "/peer_" + std::to_string(me.port) + "_output.txt", std::ios::app);
+        const std::time_t t0 = (std::time_t)gossip::kEpochSeconds;
+        f << gossip::peer_log_line(t0, "Peer node started on port " + std::to_string(me.port));  // peer.cpp:61
+        for (uint64_t e = rp[v]; e < rp[v + 1]; ++e) {                                             // peer.cpp:248
+            const PeerInfo p = peerInfo(col[e] & 0x7FFFFFFFu);
+            f << gossip::peer_log_line(t0, "Connected to peer: " + p.ip + ":" + std::to_string(p.port));
+        }
+        std::map<long, std::vector<std::string>> events;
+        const auto it = dropped.find((uint32_t)v);
+        if (it != dropped.end())
+            for (const auto& d : it->second) {                                                     // peer.cpp:389
+                const PeerInfo p = peerInfo(d.second);
+                events[d.first].push_back("Peer disconnected: " + p.ip + ":" + std::to_string(p.port));
+            }
+        for (uint32_t m = 0; m < M_; ++m) {
+            const long r = receiptRound(v, m);
+            if (r < 0) continue;
+            const bool own = origin_[m] == v && (long)injectRound_[m] == r;
+            events[r].push_back((own ? "Generated message: " : "Received new message: ") + msgs[m].content);
+        }
+        for (const auto& kv : events)
+            for (const std::string& s : kv.second) f << gossip::peer_log_line(t0 + kv.first, s);
+    }
+}
+
 void GossipNetwork::writeLogs(const std::string& dir) const {
-    if (!trace_ || opt_.n_peers > 60000) return;
+    if (opt_.n_peers > 60000) return;
+    if (!trace_ && opt_.device_trace) return writeDeviceLogs(dir);
+    if (!trace_) return;
     std::vector<Message> msgs;
     for (uint32_t m = 0; m < M_; ++m) msgs.push_back(message(m));
     for (uint64_t v = 0; v < opt_.n_peers; ++v) {

@@ -1,5 +1,6 @@
 // surface_capi.cpp -- extern "C" probes of the drop-in surface for the test
-// harness (ctypes): NetworkConfig outcomes and the reference string formats.
+// harness (ctypes): NetworkConfig outcomes, the reference string formats and
+// GossipNetwork's receipt-round view.
 #include <cstring>
 #include <exception>
 #include <string>
@@ -8,6 +9,7 @@
 
 #include "gossip/config.hpp"
 #include "gossip/formats.hpp"
+#include "gossip/network.hpp"
 #include "gossip/seed.hpp"
 
 namespace {
@@ -129,6 +131,25 @@ int gossip_surface_seed_logged(const char* ops, const char* logdir, char* out, s
 int gossip_surface_log(int seed_style, long long t, const char* msg, char* out, size_t cap) {
     return put(seed_style ? gossip::seed_log_line((std::time_t)t, msg) : gossip::peer_log_line((std::time_t)t, msg), out,
                cap);
+}
+
+// Runs the network that a network.txt describes to its end and gives GossipNetwork::receiptRound(peers[i], m)
+// for every message: out[n * M] (-1: never), *n_msgs = M.  0: ok; -1: the run failed; -2: cap < n * M entries.
+int gossip_surface_receipt_rounds(const char* path, const unsigned long long* peers, unsigned n, int* out, size_t cap,
+                                  unsigned* n_msgs) {
+    try {
+        NetworkConfig c(path);
+        auto net = std::make_shared<GossipNetwork>(c, SimOptions::fromConfig(c));
+        if (!net->run() || !net->finished()) return -1;
+        const unsigned M = net->messages();
+        if (n_msgs) *n_msgs = M;
+        if (!out || cap < (size_t)n * M) return -2;
+        for (unsigned i = 0; i < n; ++i)
+            for (unsigned m = 0; m < M; ++m) out[(size_t)i * M + m] = (int)net->receiptRound(peers[i], m);
+        return 0;
+    } catch (const std::exception&) {
+        return -1;
+    }
 }
 
 }  // extern "C"
